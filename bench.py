@@ -2,6 +2,7 @@
 """ALVRL hot-path benchmark (BASELINE.json metric) on N MI355X, one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C1]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -10,6 +11,15 @@ A step is one progressive pass of the vrl integrator over the whole frame
 VRLs (the vrlFile mode) the prepass is the LightSlice work (representative
 sampling, R build, per-slice refinement) for the clustered configs and nothing
 for the brute-force one; the render is the per-pixel gather.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value,
+ms_per_step, the steps' own kernel times and rooflines).  --dump-outputs DIR
+also writes the frame of the last timed step to DIR/framebuffer.npy (H x W x 3
+float32, what a caller of prepass + render receives); the inputs are seeded,
+so two builds can be compared frame for frame.  Everything that takes runs of
+its own is behind --full: the CPU baseline and the per-pixel RMSE against it,
+the records-mode timing, the comparison with the oracle's own pipeline, and at
+N > 1 the second decomposition.
 
 Multi-GPU (--shard):
   slices (default)  one pass per step, sharded inside the pass (BASELINE.json
@@ -25,7 +35,7 @@ Multi-GPU (--shard):
                     xGMI sums the N passes' framebuffers into rank 0 -- the
                     progressive accumulation (integrator.cpp:396-433) spread
                     over GPUs.  Per-GPU work is fixed: "scaling": "weak".
-With N > 1 and slices, the same run also times the passes decomposition
+With --full, N > 1 and slices, the same run also times the passes decomposition
 (W + K more steps) and reports it as "alt_decomposition" beside the line
 (--no-alt skips it); "value" is always the slices measurement.
 """
@@ -76,20 +86,30 @@ def parse():
     ap.add_argument("--config", default="C4", choices=sorted(CONFIGS))
     ap.add_argument("--shard", default="slices", choices=["passes", "slices"],
                     help="multi-GPU decomposition (see the module docstring)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame to DIR/framebuffer.npy (float32, H x W x 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the CPU "
+                         "baseline and RMSE against it, records mode, the oracle-pipeline comparison, "
+                         "and at N > 1 the other decomposition (the --no-* options drop single legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline and every leg that builds on it")
     ap.add_argument("--no-alt", action="store_true",
-                    help="N > 1 with --shard slices: skip the second, pass-parallel measurement")
+                    help="--full, N > 1 with --shard slices: skip the second, pass-parallel measurement")
     ap.add_argument("--no-records-mode", action="store_true",
-                    help="clustered configs: skip timing the host-cast (records mode) pipeline")
+                    help="--full, clustered configs: skip timing the host-cast (records mode) pipeline")
     ap.add_argument("--no-unconditional", action="store_true",
-                    help="clustered configs: skip the comparison with the oracle's own pipeline")
+                    help="--full, clustered configs: skip the comparison with the oracle's own pipeline")
     ap.add_argument("--cpu-row-stride", type=int, default=64,
                     help="CPU baseline sample: every n-th image row")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "r06", "pmc_traffic.json"),
                     help="per-launch HBM bytes of the dominant kernel from a rocprofv3 --pmc pass")
     ap.add_argument("--valu-json", default=os.path.join(REPO, "profiles", "r06", "pmc_valu_{cfg}.json"),
                     help="per-kernel VALU counters (tools/pmc_valu.sh + tools/pmc_valu.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def aggregate_over_ranks(elapsed, counts, world, device):
@@ -204,11 +224,18 @@ def main():
 
     value = contrib / elapsed
 
+    # the frame of the last timed step, as the caller of prepass + render
+    # receives it (rank 0 holds the reduced frame), before any other leg runs
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "framebuffer.npy"),
+                fb.view(H, W, 3).cpu().numpy().astype(np.float32, copy=False))
+
     # N > 1: the other decomposition too, on the same ranks and scene
     # (reported beside the line, never as its value): whole progressive
     # passes per GPU and one framebuffer reduce, which scales weakly
     alt = None
-    if world > 1 and by_slices and not args.no_alt:
+    if args.full and world > 1 and by_slices and not args.no_alt:
         base = args.warmup + args.steps
         for i in range(args.warmup):
             step(base + i, by_slices=False)
@@ -354,7 +381,7 @@ def main():
         }
         if alt is not None:
             out["alt_decomposition"] = alt
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], out["pixel_rmse_vs_cpu"] = cpu_baseline(args, cfg, scene, vrls, pc, fb, it,
                                                                        clustered)
         if clustered:

@@ -6,7 +6,9 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cfg=${1:-C4}
+OUT=${ALVRL_OUT:-$R/results}   # where the logs and result lines go
+mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d "$R/gpurun_out/pmc_${cfg}_$c" -o run --output-format csv -- python3 "$R/bench.py" --config $cfg --steps 1 --warmup 0 --no-cpu-baseline > "$R/gpurun_out/pmc_${cfg}_$c.log" 2>&1 || exit $?
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d "$OUT/pmc_${cfg}_$c" -o run --output-format csv -- python3 "$R/bench.py" --config $cfg --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/pmc_${cfg}_$c.log" 2>&1 || exit $?
 done
