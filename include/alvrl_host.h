@@ -93,7 +93,9 @@ ALVRL_API int alvrl_scene_records(const alvrl_scene_desc *s, int medium_scatters
 
 /* The same records on the current HIP device (Sensor::sampleRay +
  * Scene::rayIntersect through the occluder BVH: the GPU eye-ray first hit),
- * bit-identical to alvrl_scene_records.  d_pixel_ids: device array (NULL:
+ * bit-identical to alvrl_scene_records on every scene, mirror, null and
+ * dielectric occluders included (a delta surface's record carries
+ * ALVRL_REC_DELTA and a zero albedo).  d_pixel_ids: device array (NULL:
  * pixels 0..n-1); d_out: n device records, written on 'stream' (NULL: the
  * null stream); returns after they are written. */
 ALVRL_API int alvrl_scene_records_gpu(const alvrl_scene_desc *s, int medium_scatters, const uint32_t *d_pixel_ids,
@@ -129,6 +131,36 @@ ALVRL_API int alvrl_scene_records_spp_gpu(const alvrl_scene_desc *s, int medium_
 ALVRL_API int alvrl_scene_chain_spp(const alvrl_scene_desc *s, int medium_scatters, uint32_t seed, uint32_t pass,
                                     int spec_rr_depth, float init_throughput, int x, int y, uint32_t sample,
                                     uint32_t spp, alvrl_gather_rec *out, uint32_t cap, uint32_t *n);
+/* alvrl_scene_chain_spp for n pixels at once on the current HIP device
+ * (csrc/tracer.hip): one lane per pixel walks LiInternal's tree in the host's
+ * depth-first order, so every record -- its 80 bytes, its pre-order index k
+ * in the depth word, the roulette drawn from (pixel, k | sample << 16), the
+ * cap of 256 records -- is the host's bit for bit.  d_pixel_ids: device array
+ * (NULL: pixels 0..n-1).
+ *   Output in the form the integrator consumes: record 0 of a pixel is its
+ * primary record (alvrl_scene_records_spp_gpu) and is not written; the
+ * records of index k >= 1 are grouped by level d = k - 1, and within a level
+ * they follow the order of the input pixels.  level_off (host,
+ * ALVRL_CHAIN_MAX_LEVELS + 1 entries): level d is d_recs[level_off[d] ..
+ * level_off[d + 1]); *n_levels = deepest level with a record, + 1; *total =
+ * records of all levels.  d_src[r] = index into the input pixels of record
+ * r's pixel.  d_counts (device, n entries, may be NULL): records per pixel,
+ * record 0 included (0: the sensor ray hit nothing).  d_recs == NULL: size
+ * query (counts, level_off, *total); else ALVRL_ERR_INVALID if cap < *total
+ * (which is set).
+ *   A lane keeps the refracted siblings still to visit on a stack of
+ * stack_cap entries (0: the default, 8; at most 255).  A pixel whose tree
+ * needs more is not truncated: the kernel reports it, alvrl_scene_chain_spp's
+ * host code forms that pixel's path and the entry point splices it in, so
+ * the result never depends on stack_cap; *n_overflow (may be NULL) = such
+ * pixels.  Stream-ordered on 'stream'; returns after the records are written. */
+#define ALVRL_CHAIN_MAX_LEVELS 255u
+ALVRL_API int alvrl_scene_chains_gpu(const alvrl_scene_desc *s, int medium_scatters, uint32_t seed, uint32_t pass,
+                                     int spec_rr_depth, float init_throughput, uint32_t sample, uint32_t spp,
+                                     const uint32_t *d_pixel_ids, uint32_t n, uint32_t stack_cap,
+                                     uint32_t *d_counts, uint32_t *level_off, uint32_t *n_levels,
+                                     alvrl_gather_rec *d_recs, uint32_t *d_src, uint64_t cap, uint64_t *total,
+                                     uint32_t *n_overflow, void *stream);
 /* The slicing record of pixel (x, y) (buildSlices, Preprocessor.cpp:1140-1170):
  * the first hit that is not a null surface; HIT flag, position and normal. */
 ALVRL_API int alvrl_scene_slice_record(const alvrl_scene_desc *s, int x, int y, alvrl_gather_rec *out);
@@ -167,8 +199,10 @@ ALVRL_API int alvrl_trace_vrls(const alvrl_scene_desc *s, uint32_t seed, uint32_
                                uint32_t target, int short_vrls, int max_depth, int rr_depth,
                                float *soa, uint32_t cap, uint32_t *n, uint64_t *particles);
 /* The same walk on the current HIP device (csrc/tracer.hip, SURVEY 8(f) row
- * 2): one lane per particle, bit-identical VRL set and particle count.
- * soa == NULL: size query (*n, *particles). */
+ * 2): one lane per particle, bit-identical VRL set and particle count on
+ * every scene the host tracer takes -- particles reflect off mirrors, pass
+ * null interfaces and reflect off or refract through dielectrics on the
+ * device too.  soa == NULL: size query (*n, *particles). */
 ALVRL_API int alvrl_trace_vrls_gpu(const alvrl_scene_desc *s, uint32_t seed, uint32_t pass,
                                    uint32_t target, int short_vrls, int max_depth, int rr_depth,
                                    float *soa, uint32_t cap, uint32_t *n, uint64_t *particles);
@@ -394,6 +428,10 @@ typedef struct {
     /* host wall time of the last prepass's device allocations (R and its row
      * tables grown with hipMalloc; zero once they are large enough) */
     double ms_alloc;
+    /* which path ran: 1 if the last prepass traced its VRLs on the device
+     * (gpuTracer), 1 if the last prepass / render formed the eye paths' delta
+     * chains on the device (gpuChains; 0 on a scene without delta surfaces) */
+    uint32_t traced_on_device, chains_on_device;
 } alvrl_integrator_stats;
 ALVRL_API int alvrl_integrator_get_stats(alvrl_integrator *it, alvrl_integrator_stats *st);
 /* The device context the integrator drives (for low-level access). */

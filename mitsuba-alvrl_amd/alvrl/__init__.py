@@ -473,7 +473,8 @@ class IntegratorStats(C.Structure):
                 ("fallback_built", C.c_int), ("slices_local", C.c_uint64), ("rows_built", C.c_uint64),
                 ("ms_exchange", C.c_double), ("ms_refine_kernel", C.c_double),
                 ("refine_entries", C.c_uint64), ("global_clusters", C.c_uint64),
-                ("refine_split_entries", C.c_uint64), ("ms_alloc", C.c_double)]
+                ("refine_split_entries", C.c_uint64), ("ms_alloc", C.c_double),
+                ("traced_on_device", C.c_uint32), ("chains_on_device", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -882,6 +883,51 @@ def scene_records_spp_gpu(scene: SceneDesc, spp: int, pixel_ids=None, medium_sca
         _hcheck(L.alvrl_scene_records_spp_gpu(C.byref(scene), int(medium_scatters), seed, pass_, spp,
                                               None if ids is None else ids.data_ptr(), n, out.data_ptr(), stream))
     return out
+
+
+CHAIN_MAX_LEVELS = 255
+
+
+def scene_chains_gpu(scene: SceneDesc, pixel_ids=None, medium_scatters: bool = True, seed: int = 0xA1B2C3D4,
+                     pass_: int = 0, spec_rr_depth: int = 100, init_throughput: float = 20.0, sample: int = 0,
+                     spp: int = 1, stack_cap: int = 0, device: int = 0) -> dict:
+    """alvrl_scene_chains_gpu: scene_chain_spp for many pixels on the HIP device.
+    Returns numpy arrays: "counts" (records per pixel, record 0 included),
+    "level_off" (level d = records of index d + 1 is recs[level_off[d]:
+    level_off[d + 1]], in the order of the pixels), "recs" ((total, REC_WORDS),
+    the records of index >= 1), "src" (each record's index into the pixels),
+    and "overflow": the pixels whose pending-sibling stack exceeded stack_cap
+    (0: the default) and were completed by the host's code."""
+    import torch
+    L = _host()
+    u32, u64, i32, f32, vp = C.c_uint32, C.c_uint64, C.c_int, C.c_float, C.c_void_p
+    L.alvrl_scene_chains_gpu.argtypes = [C.POINTER(SceneDesc), i32, u32, u32, i32, f32, u32, u32, vp, u32, u32, vp,
+                                         C.POINTER(u32), C.POINTER(u32), vp, vp, u64, C.POINTER(u64),
+                                         C.POINTER(u32), vp]
+    dev = torch.device("cuda", device)
+    n = scene.width * scene.height if pixel_ids is None else len(pixel_ids)
+    ids = None if pixel_ids is None else torch.as_tensor(np.asarray(pixel_ids, np.uint32).astype(np.int32)).to(dev)
+    counts = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    lo = (u32 * (CHAIN_MAX_LEVELS + 1))()
+    nl, novf, total = u32(), u32(), u64()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def call(recs, src, cap):
+            _hcheck(L.alvrl_scene_chains_gpu(C.byref(scene), int(medium_scatters), seed, pass_, spec_rr_depth,
+                                             float(init_throughput), sample, spp,
+                                             None if ids is None else ids.data_ptr(), n, stack_cap, counts.data_ptr(),
+                                             lo, C.byref(nl), recs, src, cap, C.byref(total), C.byref(novf), stream))
+        call(None, None, 0)   # size query
+        t = int(total.value)
+        recs = torch.zeros((max(t, 1), REC_WORDS), dtype=torch.float32, device=dev)
+        src = torch.zeros(max(t, 1), dtype=torch.int32, device=dev)
+        call(recs.data_ptr(), src.data_ptr(), t)
+        torch.cuda.synchronize(dev)
+    return {"counts": counts[:n].cpu().numpy().view(np.uint32),
+            "level_off": np.asarray(lo[:nl.value + 1], np.uint32),
+            "recs": recs[:t].cpu().numpy(), "src": src[:t].cpu().numpy().view(np.uint32),
+            "overflow": int(novf.value)}
 
 
 class VolpathParams(C.Structure):

@@ -80,9 +80,41 @@ struct DevBuf {
         hchk(hipMalloc(&p, std::max<size_t>(cnt, 1) * sizeof(T)), "hipMalloc");
         n = cnt;
     }
+    // grow to cnt elements (with slack), keeping the first 'keep' (as far as the buffer holds them)
+    void grow_keep(size_t cnt, size_t keep)
+    {
+        if (cnt <= n && p) return;
+        keep = std::min(keep, n);
+        const size_t want = cnt + cnt / 8;
+        T* q = nullptr;
+        hchk(hipMalloc(&q, std::max<size_t>(want, 1) * sizeof(T)), "hipMalloc");
+        if (p && keep) {
+            const hipError_t e = hipMemcpy(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) { hipFree(q); hchk(e, "copy"); }
+        }
+        if (p) hipFree(p);
+        p = q;
+        n = want;
+    }
     ~DevBuf() { if (p) hipFree(p); }
 };
 }  // namespace
+
+// flags |= bits on n gather records (the R build's ALVRL_REC_ACCUM levels)
+__global__ void __launch_bounds__(256) k_or_flags(alvrl_gather_rec* __restrict__ r, uint32_t n, uint32_t bits)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) r[i].flags |= bits;
+}
+
+// dst[i] = src[idx[i]]: a level's records into their slice-bucketed order
+__global__ void __launch_bounds__(256) k_gather_recs(alvrl_gather_rec* __restrict__ dst,
+                                                     const alvrl_gather_rec* __restrict__ src,
+                                                     const uint32_t* __restrict__ idx, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[idx[i]];
+}
 
 __global__ void __launch_bounds__(256) k_scale_f32(float* __restrict__ v, uint32_t n, float f)
 {
@@ -118,9 +150,12 @@ struct alvrl_integrator {
     int rrDepth = 5, maxDepth = -1;
     uint32_t seed = 0xA1B2C3D4u, vrlSeed = 0x5EED0001u;
     // trace the pass's VRLs on the device (csrc/tracer.hip, bit-identical to
-    // the host tracer) wherever the scene fits it -- no mirror / null /
-    // dielectric triangles, whose particles the host traces; false: always the host
+    // the host tracer on every scene, delta surfaces included); false: the host
     bool gpuTracer = true;
+    // form the eye paths' delta-BSDF chains on the device
+    // (alvrl_scene_chains_gpu, bit-identical to SmokeBox::make_chain) and keep
+    // their records there; false: the host's threads
+    bool gpuChains = true;
     bool strictRbuild = true;
     // slices to ranks with world > 1: "cost" (longest processing time first on
     // each slice's local rows, the default) or "roundrobin" (s % world)
@@ -176,6 +211,10 @@ struct alvrl_integrator {
     DevBuf<alvrl_gather_rec> ch_recs;
     DevBuf<uint32_t> ch_ids, ch_stride;
     DevBuf<uint64_t> ch_off;
+    // gpuChains: the records' source indices, the frame's pixels on the
+    // device, and the staging of a sample's records for their slice bucketing
+    DevBuf<uint32_t> ch_src, chain_pix, perm_idx;
+    DevBuf<alvrl_gather_rec> perm_tmp;
     std::vector<uint32_t> level_rec;        // render: first record of each depth level (+ end)
     std::vector<uint32_t> level_item;       // render: first work item of each level (+ end)
     DevBuf<alvrl_gather_rec> rec_buf;
@@ -213,6 +252,7 @@ struct alvrl_integrator {
         if (k == "nc") throw IntegError(ALVRL_ERR_INVALID, "Neighbourcount is now called 'neighbourCount' instead of 'nc'!");
         else if (k == "shortVrls") shortVrls = b(v);
         else if (k == "gpuTracer") gpuTracer = b(v);
+        else if (k == "gpuChains") gpuChains = b(v);
         else if (k == "strictRbuild") strictRbuild = b(v);
         else if (k == "sliceSharding") {
             if (v != "cost" && v != "roundrobin") throw IntegError(ALVRL_ERR_INVALID, "sliceSharding must be cost or roundrobin");
@@ -426,6 +466,7 @@ struct alvrl_integrator {
         if (world > 1 && (!ex || !ex->allgather)) throw IntegError(ALVRL_ERR_INVALID, "world > 1 needs an alvrl_exchange");
         if (!have_scene) throw IntegError(ALVRL_ERR_STATE, "prepass before preprocess");
         const double tw = now_ms();
+        st.chains_on_device = 0;
         pass_vrls(pass);
         st.slices_failed = 0;
         st.fallback_built = 0;
@@ -453,7 +494,8 @@ struct alvrl_integrator {
             const double t0 = now_ms();
             const alvrl_scene_desc& td = ext ? tracer_desc : scene_desc;
             const SmokeBox& tb = ext ? tracer_box : scene;
-            if (gpuTracer && !tb.has_delta()) {
+            st.traced_on_device = gpuTracer ? 1u : 0u;
+            if (gpuTracer) {
                 const uint32_t target = (uint32_t)std::max(vrlTargetNum, 0);
                 uint32_t n = 0;
                 uint64_t pc = 0;
@@ -541,12 +583,13 @@ struct alvrl_integrator {
     }
 
     // LiInternal's specular chains (:445-511) of the given row-major pixels,
-    // traced on the host (SmokeBox::make_chain, the occluders are few):
+    // the host form (gpuChains=false; chains_dev below is the device's):
+    // SmokeBox::make_chain on up to 16 threads:
     // recs[d - 1] = the records of depth d >= 1 (their path weights
     // transmittance * bsdfWeight / rrProb multiplied along the chain), src =
     // the index into ids of each; prim[i] = the primary record of ids[i]
-    // (the device's eye-ray kernel knows no materials).  The Russian roulette
-    // draws from the pass's (seed, pass, pixel, depth) stream.
+    // (SmokeBox::make_record).  The Russian roulette draws from the pass's
+    // (seed, pass, pixel, depth) stream.
     struct Chains {
         std::vector<std::vector<alvrl_gather_rec>> recs;
         std::vector<std::vector<uint32_t>> src;
@@ -599,6 +642,40 @@ struct alvrl_integrator {
             }
         }
         return out;
+    }
+
+    // expand_chains' deeper records on the device (gpuChains): the eye paths
+    // of the n pixels d_ids (device), sensor sample `sample` of `spp`, through
+    // alvrl_scene_chains_gpu -- the host's records bit for bit, level by
+    // level, in the order of the pixels.  They stay on the device, in buf
+    // from element `at` on (buf grows, keeping what lies before); lv = the
+    // levels' offsets relative to `at` (+ end), src = each record's index
+    // into the pixels (host copy, for the per-record tables of the caller).
+    void chains_dev(const uint32_t* d_ids, uint32_t n, bool scat, uint32_t sample, uint32_t spp,
+                    DevBuf<alvrl_gather_rec>& buf, size_t at, std::vector<uint32_t>* lv, std::vector<uint32_t>* src)
+    {
+        uint32_t lo[ALVRL_CHAIN_MAX_LEVELS + 1], nl = 0;
+        uint64_t total = 0;
+        buf.grow_keep(at + 1, at);
+        for (int attempt = 0;; attempt++) {
+            const uint64_t cap = buf.n - at;
+            ch_src.ensure(cap);
+            const int rc = alvrl_scene_chains_gpu(&scene_desc, scat ? 1 : 0, seed, cur_pass, specRRdepth,
+                                                  initialSpecularThroughput, sample, spp, d_ids, n, 0, nullptr, lo, &nl,
+                                                  buf.p + at, ch_src.p, cap, &total, nullptr, stream);
+            if (rc == ALVRL_OK) break;
+            if (attempt > 0 || total <= cap) chk_host(rc);
+            // the one refusal that is no error: more records than buf held.  buf
+            // keeps its size (and slack) from pass to pass, so this second walk is
+            // paid only where the frame grows; asking for the size first would
+            // pay a second count pass on every frame
+            buf.grow_keep(at + total, at);
+            g_host_err.clear();
+        }
+        lv->assign(lo, lo + nl + 1);
+        src->resize(total);
+        if (total)
+            hchk(hipMemcpy(src->data(), ch_src.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost), "copy chain sources");
     }
 
     // The host's records of the built rows gl[i] (alvrl_integrator_prepass_records),
@@ -672,6 +749,7 @@ struct alvrl_integrator {
             acc += n;
         }
         const uint32_t nb = (uint32_t)ids.size();
+        const bool dev_chains = chains && gpuChains && !ext;   // the rows' eye paths on the device
         rows_built = nb;
         const double ta = now_ms();
         rep_recs.ensure(nb);
@@ -683,7 +761,8 @@ struct alvrl_integrator {
         st.ms_alloc += now_ms() - ta;
         if (nb) {
             hchk(hipMemcpyAsync(rep_ids.p, ids.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, stream), "copy rep ids");
-            if (!chains && !ext) chk_host(alvrl_scene_records_gpu(&scene_desc, scat ? 1 : 0, rep_ids.p, nb, rep_recs.p, stream));
+            if ((!chains && !ext) || dev_chains)
+                chk_host(alvrl_scene_records_gpu(&scene_desc, scat ? 1 : 0, rep_ids.p, nb, rep_recs.p, stream));
             hchk(hipMemcpyAsync(rb_off.p, boff.data(), sizeof(uint64_t) * nb, hipMemcpyHostToDevice, stream), "copy row offsets");
             hchk(hipMemcpyAsync(rb_stride.p, bstr.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, stream), "copy row strides");
         }
@@ -693,7 +772,27 @@ struct alvrl_integrator {
         // records flagged ALVRL_REC_ACCUM (a row has at most one record per level)
         Chains ch;
         std::vector<uint32_t> lv_off{0};
-        if ((chains || ext) && nb) {
+        if (dev_chains && nb) {
+            // the levels' records are formed on the device and stay there;
+            // only their row tables come from the host
+            st.chains_on_device = 1;
+            std::vector<uint32_t> src;
+            chains_dev(rep_ids.p, nb, scat, 0, 1, ch_recs, 0, &lv_off, &src);
+            const size_t n = src.size();
+            if (n) {
+                std::vector<uint32_t> cid(n), cstr(n);
+                std::vector<uint64_t> coff(n);
+                for (size_t j = 0; j < n; j++) { cid[j] = ids[src[j]]; coff[j] = boff[src[j]]; cstr[j] = bstr[src[j]]; }
+                ch_ids.ensure(n); ch_off.ensure(n); ch_stride.ensure(n);
+                hipLaunchKernelGGL(k_or_flags, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, stream, ch_recs.p,
+                                   (uint32_t)n, (uint32_t)ALVRL_REC_ACCUM);
+                hchk(hipGetLastError(), "k_or_flags");
+                hchk(hipMemcpyAsync(ch_ids.p, cid.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, stream), "copy chain ids");
+                hchk(hipMemcpyAsync(ch_off.p, coff.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, stream), "copy chain offsets");
+                hchk(hipMemcpyAsync(ch_stride.p, cstr.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, stream), "copy chain strides");
+                hchk(hipStreamSynchronize(stream), "sync");   // cid, coff, cstr are freed here
+            }
+        } else if ((chains || ext) && nb) {
             std::vector<alvrl_gather_rec> prim;
             if (ext) ch = host_rows(gl, rows, &prim);
             else ch = expand_chains(ids, scat, true, &prim);
@@ -999,6 +1098,8 @@ struct alvrl_integrator {
         const uint32_t mode = clustered ? 2u : 1u;
         // chains (their Russian roulette) and sensor samples depend on the pass
         const uint32_t S = (uint32_t)sampleCount;
+        // the frame's chains, formed now or held in the cache, are the device's with gpuChains
+        if (chains && gpuChains) st.chains_on_device = 1;
         if (cache_rank == rank && cache_world == world && cache_mode == mode &&
             ((!chains && S == 1) || cache_pass == cur_pass))
             return;
@@ -1071,7 +1172,45 @@ struct alvrl_integrator {
         }
         std::vector<alvrl_gather_rec> extra;   // the chains' records, level by level
         std::vector<alvrl_gather_rec> prim;
-        if (chains) {
+        const bool dev_chains = chains && gpuChains;   // (a host-cast scene never renders here)
+        if (dev_chains) {
+            // every sample's deeper records straight into rec_buf behind the
+            // primary blocks, level by level; a level's records are put into
+            // their slice-bucketed order on the device
+            const size_t np = (size_t)nprim * S;
+            const std::vector<uint32_t> ppix(pix.begin(), pix.begin() + nprim);
+            chain_pix.ensure(nprim);
+            if (nprim) hchk(hipMemcpy(chain_pix.p, ppix.data(), sizeof(uint32_t) * nprim, hipMemcpyHostToDevice), "copy pixels");
+            size_t used = 0;
+            for (uint32_t j = 0; j < S && nprim; j++) {
+                std::vector<uint32_t> lv, src, idx;
+                chains_dev(chain_pix.p, nprim, scat, j, S, rec_buf, np + used, &lv, &src);
+                const size_t tj = src.size();
+                if ((uint64_t)np + used + tj > 0x7FFFFFFFull) throw IntegError(ALVRL_ERR_INVALID, "too many eye-path records for the frame");
+                for (size_t d = 0; d + 1 < lv.size(); d++) {
+                    std::vector<uint32_t> recpix(lv[d + 1] - lv[d]);
+                    for (size_t k = 0; k < recpix.size(); k++) recpix[k] = ppix[src[lv[d] + k]];
+                    std::vector<uint32_t> order(recpix.size());
+                    for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
+                    if (clustered) bucket(&order, recpix, (uint32_t)(np + used) + lv[d]);
+                    for (uint32_t k : order) { pix.push_back(recpix[k]); idx.push_back(lv[d] + k); }
+                    level_rec.push_back((uint32_t)(np + used) + lv[d + 1]);
+                    level_item.push_back((uint32_t)items.size());
+                }
+                if (clustered && tj) {
+                    perm_tmp.ensure(tj);
+                    perm_idx.ensure(tj);
+                    hchk(hipMemcpyAsync(perm_tmp.p, rec_buf.p + np + used, sizeof(alvrl_gather_rec) * tj,
+                                        hipMemcpyDeviceToDevice, stream), "copy chain records");
+                    hchk(hipMemcpyAsync(perm_idx.p, idx.data(), sizeof(uint32_t) * tj, hipMemcpyHostToDevice, stream), "copy order");
+                    hipLaunchKernelGGL(k_gather_recs, dim3(((uint32_t)tj + 255) / 256), dim3(256), 0, stream,
+                                       rec_buf.p + np + used, perm_tmp.p, perm_idx.p, (uint32_t)tj);
+                    hchk(hipGetLastError(), "k_gather_recs");
+                    hchk(hipStreamSynchronize(stream), "sync");   // idx is freed here
+                }
+                used += tj;
+            }
+        } else if (chains) {
             prim.resize((size_t)nprim * S);
             const std::vector<uint32_t> ppix(pix.begin(), pix.begin() + nprim);
             for (uint32_t j = 0; j < S; j++) {
@@ -1093,12 +1232,15 @@ struct alvrl_integrator {
         }
         nrec = (uint32_t)pix.size();
         nitems = (uint32_t)items.size();
-        rec_buf.ensure(nrec);
+        if (dev_chains && nprim) {
+            if (rec_buf.n < nrec) throw IntegError(ALVRL_ERR_STATE, "chain records outgrew the record buffer");   // chains_dev sized it
+        } else
+            rec_buf.ensure(nrec);
         pix_buf.ensure(nrec);
         out_buf.ensure((size_t)3 * nrec);
         hchk(hipMemcpyAsync(pix_buf.p, pix.data(), sizeof(uint32_t) * nrec, hipMemcpyHostToDevice, stream), "copy pixels");
         // the eye-ray first hits of the owned pixels' sensor samples, on the device
-        if (chains) {
+        if (chains && !dev_chains) {
             if (nprim)
                 hchk(hipMemcpyAsync(rec_buf.p, prim.data(), sizeof(alvrl_gather_rec) * prim.size(),
                                     hipMemcpyHostToDevice, stream), "copy records");

@@ -2,7 +2,7 @@
 // SURVEY.md 8(f) row 2.  One lane per particle: particle p draws from its own
 // counter-based stream (seed, pass, p), exactly as the host tracer
 // (csrc/host/scene.cpp trace_particle) and the oracle do, so the VRL set is
-// the host's bit for bit.  Built with -ffp-contract=off and IEEE division /
+// the host's bit for bit -- diffuse, mirror, null and dielectric surfaces alike.  Built with -ffp-contract=off and IEEE division /
 // square root like the host; sin, cos, exp and log are evaluated in double
 // and rounded once, as on the host.
 //
@@ -50,6 +50,11 @@ struct TScene {
     alvrl::bvh::View bv;          // occluders (ntri == 0: none)
     float occ_albedo[3];
     const float* occ_alb;         // per-triangle reflectance (3 floats, by triangle index), or nullptr
+    // delta BSDFs (SmokeBox::occ_mat / occ_spec / occ_eta): the per-triangle
+    // ALVRL_MAT_* table on the device (nullptr: every triangle diffuse), the
+    // mirrors' reflectance, the dielectrics' intIOR / extIOR
+    const uint32_t* occ_mat;
+    float occ_spec[3], occ_eta;
     // area emitter (SmokeBox::emit; nemit == 0: the point light): triangles,
     // the normalized area CDF (nemit + 1 entries), radiance and surface area
     const float* emit;
@@ -248,6 +253,33 @@ __device__ __forceinline__ const float* albedo_of(const TScene& sc, int tri)
     return tri < 0 ? sc.albedo : sc.occ_alb ? sc.occ_alb + 3 * (size_t)tri : sc.occ_albedo;
 }
 
+// the BSDF of what first_hit hit (SmokeBox::mat): 0 diffuse (the walls too), 1 mirror, 2 null, 3 dielectric
+__device__ __forceinline__ uint32_t mat_of(const TScene& sc, int tri)
+{
+    return (tri < 0 || !sc.occ_mat) ? 0u : sc.occ_mat[(size_t)tri];
+}
+
+// fresnelDielectricExt (util.cpp:651-681), the host's fresnel_dielectric_ext operation for operation
+__device__ float fresnel_dielectric_ext(float cos_theta_i, float* cos_theta_t, float eta)
+{
+    if (eta == 1) {
+        *cos_theta_t = -cos_theta_i;
+        return 0.0f;
+    }
+    const float scale = (cos_theta_i > 0) ? 1 / eta : eta;
+    const float cos_t_sqr = 1 - (1 - cos_theta_i * cos_theta_i) * (scale * scale);
+    if (cos_t_sqr <= 0.0f) {   // total internal reflection
+        *cos_theta_t = 0.0f;
+        return 1.0f;
+    }
+    const float ci = fabsf(cos_theta_i);
+    const float ct = sqrtf(cos_t_sqr);
+    const float Rs = (ci - eta * ct) / (ci + eta * ct);
+    const float Rp = (eta * ci - ct) / (eta * ci + ct);
+    *cos_theta_t = (cos_theta_i > 0) ? -ct : ct;
+    return 0.5f * (Rs * Rs + Rp * Rp);
+}
+
 // vrlVector::put + the current VRL (vrlTracer.h:56-89, VRL.h:148-158); counts,
 // or writes into the SoA planes at 'pos' when soa != nullptr
 struct Sink {
@@ -323,8 +355,10 @@ __device__ void trace_particle(const TScene& sc, Stream& smp, bool short_vrls, i
     for (int i = 0; i < 3; i++) k.power[i] = power[i];
     int depth = 1;
     float thr[3] = {1.0f, 1.0f, 1.0f};
-    const float eta = 1.0f;
+    float eta = 1.0f;
     float mint = 1e-4f;   // Ray() default mint (Epsilon), then 0 after a medium and Epsilon after a surface
+    // bounded like the host's loop: max_depth when set, else the roulette from
+    // rr_depth on (survival <= 0.95 per iteration) and the throughput reaching 0
     while (!(thr[0] == 0 && thr[1] == 0 && thr[2] == 0) && (depth <= max_depth || max_depth < 0)) {
         F3 n, hp;
         int hit_tri;
@@ -374,9 +408,32 @@ __device__ void trace_particle(const TScene& sc, Stream& smp, bool short_vrls, i
             const float bx = smp.next(), by = smp.next();
             float bw[3] = {0, 0, 0};
             F3 wol = f3(0, 0, 0);
-            if (!(cos_wi <= 0)) {
-                wol = cosine_hemisphere(bx, by);
-                for (int i = 0; i < 3; i++) bw[i] = alb[i];
+            const uint32_t mt = mat_of(sc, hit_tri);
+            if (mt == 0u) {          // SmoothDiffuse::sample (diffuse.cpp:120-133)
+                if (!(cos_wi <= 0)) {
+                    wol = cosine_hemisphere(bx, by);
+                    for (int i = 0; i < 3; i++) bw[i] = alb[i];
+                }
+            } else if (mt == 1u) {   // SmoothConductor::sample (conductor.cpp:254-268), material none
+                if (!(cos_wi <= 0)) {
+                    wol = f3(-dot(mwi, fs), -dot(mwi, ft), cos_wi);   // reflect(wi)
+                    for (int i = 0; i < 3; i++) bw[i] = sc.occ_spec[i];
+                }
+            } else if (mt == 3u) {   // SmoothDielectric::sample, both components, EImportance (dielectric.cpp:335-364)
+                float cos_t;
+                const float F = fresnel_dielectric_ext(cos_wi, &cos_t, sc.occ_eta);
+                if (bx <= F) {
+                    wol = f3(-dot(mwi, fs), -dot(mwi, ft), cos_wi);
+                } else {
+                    const float inv_eta = 1 / sc.occ_eta;
+                    const float scale = -(cos_t < 0 ? inv_eta : sc.occ_eta);   // refract(wi, cosThetaT)
+                    wol = f3(scale * dot(mwi, fs), scale * dot(mwi, ft), cos_t);
+                    eta *= cos_t < 0 ? sc.occ_eta : inv_eta;                   // bRec.eta
+                }
+                bw[0] = bw[1] = bw[2] = 1.0f;                                 // importance: factor 1
+            } else {                 // Null::sample (null.cpp:53-63): wo = -wi
+                wol = f3(-dot(mwi, fs), -dot(mwi, ft), -cos_wi);
+                bw[0] = bw[1] = bw[2] = 1.0f;
             }
             if (bw[0] == 0 && bw[1] == 0 && bw[2] == 0) { k.end_current(p); break; }
             const F3 wo = add(add(mul(fs, wol.x), mul(ft, wol.y)), mul(n, wol.z));
@@ -528,16 +585,10 @@ __device__ __forceinline__ void pixel_jitter(uint32_t seed, uint32_t pass, uint3
     *v = __uint_as_float((c1 >> 9) | 0x3f800000u) - 1.0f;
 }
 
-// spp records per pixel, sample major: record j * n + i is pixel pix[i],
-// sensor sample j (its depth word j << 16); spp == 1: pixel centres.
-__global__ void __launch_bounds__(256) k_eye_records(TCam c, TScene sc, const uint32_t* __restrict__ pix,
-                                                     uint32_t n, uint32_t spp, uint32_t seed, uint32_t pass,
-                                                     float* __restrict__ out)
+// Sensor::sampleRay through sensor sample j of spp of pixel id (SmokeBox::pixel_sample + camera_ray)
+__device__ __forceinline__ void sensor_ray(const TCam& c, uint32_t id, uint32_t j, uint32_t spp, uint32_t seed,
+                                           uint32_t pass, F3* O, F3* D, float* mint)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * spp) return;
-    const uint32_t j = i / n, ii = i - j * n;
-    const uint32_t id = pix ? pix[ii] : ii;
     float px = (float)(id % c.width) + 0.5f, py = (float)(id / c.width) + 0.5f;
     if (spp > 1) {
         float u, v;
@@ -550,25 +601,297 @@ __global__ void __launch_bounds__(256) k_eye_records(TCam c, TScene sc, const ui
     const float yc = ((1.0f - 2.0f * sy) / c.aspect) * c.tanh_;
     F3 dc = f3(xc, yc, 1.0f);
     dc = mul(dc, 1.0f / len(dc));
-    const float mint = 1e-2f * (1.0f / dc.z);
-    const F3 O = f3(c.o[0], c.o[1], c.o[2]);
-    const F3 D = f3(c.left[0] * dc.x + c.nup[0] * dc.y + c.fwd[0] * dc.z,
-                    c.left[1] * dc.x + c.nup[1] * dc.y + c.fwd[1] * dc.z,
-                    c.left[2] * dc.x + c.nup[2] * dc.y + c.fwd[2] * dc.z);
+    *mint = 1e-2f * (1.0f / dc.z);
+    *O = f3(c.o[0], c.o[1], c.o[2]);
+    *D = f3(c.left[0] * dc.x + c.nup[0] * dc.y + c.fwd[0] * dc.z,
+            c.left[1] * dc.x + c.nup[1] * dc.y + c.fwd[1] * dc.z,
+            c.left[2] * dc.x + c.nup[2] * dc.y + c.fwd[2] * dc.z);
+}
+
+// spp records per pixel, sample major: record j * n + i is pixel pix[i],
+// sensor sample j (its depth word j << 16); spp == 1: pixel centres.
+__global__ void __launch_bounds__(256) k_eye_records(TCam c, TScene sc, const uint32_t* __restrict__ pix,
+                                                     uint32_t n, uint32_t spp, uint32_t seed, uint32_t pass,
+                                                     float* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * spp) return;
+    const uint32_t j = i / n, ii = i - j * n;
+    const uint32_t id = pix ? pix[ii] : ii;
+    F3 O, D;
+    float mint;
+    sensor_ray(c, id, j, spp, seed, pass, &O, &D, &mint);
     F3 nn, p;
     int tri;
     const float t = first_hit(sc, O, D, mint, &nn, &p, &tri);
+    const uint32_t m = mat_of(sc, tri);
     uint32_t flags = 0;
-    if (isfinite(t)) flags |= 1u | 2u;
+    if (isfinite(t)) flags |= 1u | (m == 0u ? 2u : 8u);   // ESmooth (diffuse) or EDelta, as SmokeBox::make_record
     if (c.scat) flags |= 4u;
     const float* a = albedo_of(sc, tri);
     float* r = out + 20 * (size_t)i;   // alvrl_gather_rec: 20 words
-    const float v[15] = {O.x, O.y, O.z, D.x, D.y, D.z, p.x, p.y, p.z, nn.x, nn.y, nn.z, a[0], a[1], a[2]};
+    const float v[15] = {O.x, O.y, O.z, D.x, D.y, D.z, p.x, p.y, p.z, nn.x, nn.y, nn.z,
+                         m == 0u ? a[0] : 0.0f, m == 0u ? a[1] : 0.0f, m == 0u ? a[2] : 0.0f};
 #pragma unroll
     for (int k = 0; k < 15; k++) r[k] = v[k];
     r[15] = __uint_as_float(flags);
     r[16] = 1.0f; r[17] = 1.0f; r[18] = 1.0f;   // a camera ray: path weight 1, depth 0
     r[19] = __uint_as_float(j << 16);
+}
+
+// ------------------------------------------------------ eye-path chains --
+// SmokeBox::chain_node (host/scene.cpp), LiInternal's recursion through delta
+// BSDFs (vrlIntegrator.cpp:398-524), as an explicit pre-order traversal: one
+// lane per pixel.  A node is one LiInternal call: the record of the ray's
+// hit, then each delta component's continuation.  The roulette stream of a
+// node is keyed by the node's own record index (seed, pass, dom 7, pixel,
+// k | sample << 16) and only that node draws from it, in component order, so
+// both children are decided when the node is visited: the lane goes on with
+// the first surviving child and, at a dielectric whose reflection and
+// refraction both survive, parks the refracted one on its pending-sibling
+// stack until the reflected subtree is finished -- the host's depth-first
+// order, which fixes every record's index.
+constexpr uint32_t kDomEye = 7u;
+constexpr uint32_t kChainMaxRecs = 256u;     // SmokeBox::chain_node's cap
+constexpr uint32_t kChainStackDefault = 8u;  // pending siblings per lane
+constexpr uint32_t kChainStackMax = 255u;    // a sibling is parked by a node that wrote a record
+constexpr uint32_t kChainOverflow = 0xFFFFFFFFu;   // the count of a pixel whose tree needs a deeper stack
+constexpr int kChainNodeWords = 13;          // p, direction, path weight, throughput, depth
+
+struct CArgs {
+    uint32_t seed, pass, sample, spp, flags, cap;   // flags: HIT | MEDIUM of every record; cap: stack entries per lane
+    int spec_rr_depth;
+    float init_thr;
+};
+
+struct CNode {
+    F3 o, d;
+    float w[3], thr[3];
+    int depth;
+};
+
+// draws 0 and 1 of the node's roulette stream (the host's Stream{seed, pass, kDomEye, pixel, kw, 0})
+__device__ __forceinline__ void eye_draws(uint32_t seed, uint32_t pass, uint32_t pixel, uint32_t kw, float u[2])
+{
+    uint32_t c0 = pixel, c1 = kw, c2 = 0u, c3 = kDomEye << 24;
+    uint32_t k0 = seed, k1 = pass;
+    for (int r = 0; r < 10; r++) {
+        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+    }
+    u[0] = __uint_as_float((c0 >> 9) | 0x3f800000u) - 1.0f;
+    u[1] = __uint_as_float((c1 >> 9) | 0x3f800000u) - 1.0f;
+}
+
+// The pending siblings of lane 'lane' of 'lanes': word w of entry e at
+// stack[(e * kChainNodeWords + w) * lanes + lane], so a wave's pushes coalesce.
+__device__ __forceinline__ void chain_push(float* stack, uint64_t lanes, uint64_t lane, uint32_t e, const CNode& nd)
+{
+    const float v[kChainNodeWords] = {nd.o.x, nd.o.y, nd.o.z, nd.d.x, nd.d.y, nd.d.z, nd.w[0], nd.w[1], nd.w[2],
+                                      nd.thr[0], nd.thr[1], nd.thr[2], __int_as_float(nd.depth)};
+#pragma unroll
+    for (int w = 0; w < kChainNodeWords; w++) stack[((uint64_t)e * kChainNodeWords + w) * lanes + lane] = v[w];
+}
+
+__device__ __forceinline__ CNode chain_pop(const float* stack, uint64_t lanes, uint64_t lane, uint32_t e)
+{
+    float v[kChainNodeWords];
+#pragma unroll
+    for (int w = 0; w < kChainNodeWords; w++) v[w] = stack[((uint64_t)e * kChainNodeWords + w) * lanes + lane];
+    CNode nd;
+    nd.o = f3(v[0], v[1], v[2]); nd.d = f3(v[3], v[4], v[5]);
+    for (int i = 0; i < 3; i++) { nd.w[i] = v[6 + i]; nd.thr[i] = v[9 + i]; }
+    nd.depth = __float_as_int(v[12]);
+    return nd;
+}
+
+// The eye path of pixel 'pixel' from the sensor ray (O, D, mint).  Returns the
+// number of records (record 0 is the primary record, which k_eye_records
+// writes), or kChainOverflow when the pending siblings exceed a.cap.  With
+// out != nullptr record k >= 1 goes to out[pos[k - 1]] and its source index
+// to src[pos[k - 1]], for k < limit only (the pixel's count from the count
+// pass: the write pass never leaves the pixel's offsets).
+__device__ uint32_t chain_walk(const TScene& sc, const CArgs& a, uint32_t pixel, F3 O, F3 D, float mint0, float* stack,
+                               uint64_t lanes, uint64_t lane, float* out, uint32_t* src, const uint32_t* pos,
+                               uint32_t limit, uint32_t src_index)
+{
+    CNode cur;
+    cur.o = O; cur.d = D;
+    for (int i = 0; i < 3; i++) { cur.w[i] = 1.0f; cur.thr[i] = a.init_thr; }   // throughputWithEtaSq (:381)
+    cur.depth = 1;
+    float mint = mint0;
+    uint32_t k = 0, sp = 0;
+    // One iteration per visited node.  Bound: a node either writes a record
+    // (at most kChainMaxRecs of them: the loop ends at k == 256, where the
+    // host's remaining calls all return at once) or ends its branch and pops
+    // a sibling (at most one per record written), so <= 512 iterations.
+    while (k < kChainMaxRecs) {
+        bool alive = false;
+        CNode next;
+        F3 n, p;
+        int tri;
+        const float t = first_hit(sc, cur.o, cur.d, mint, &n, &p, &tri);
+        if (isfinite(t)) {                                                   // :414-419
+            const uint32_t m = mat_of(sc, tri);
+            const uint32_t kw = k | (a.sample << 16);
+            if (out && k >= 1 && k < limit) {
+                const float* al = albedo_of(sc, tri);
+                float* r = out + 20 * (size_t)pos[k - 1];
+                const float v[15] = {cur.o.x, cur.o.y, cur.o.z, cur.d.x, cur.d.y, cur.d.z, p.x, p.y, p.z, n.x, n.y, n.z,
+                                     m == 0u ? al[0] : 0.0f, m == 0u ? al[1] : 0.0f, m == 0u ? al[2] : 0.0f};
+#pragma unroll
+                for (int q = 0; q < 15; q++) r[q] = v[q];
+                r[15] = __uint_as_float(a.flags | (m == 0u ? 2u : 8u));
+                r[16] = cur.w[0]; r[17] = cur.w[1]; r[18] = cur.w[2];
+                r[19] = __uint_as_float(kw);
+                src[pos[k - 1]] = src_index;
+            }
+            ++k;
+            float tr[3] = {0.0f, 0.0f, 0.0f};
+            if (m != 0u) {   // the segment's transmittance (:450-460); a diffuse hit has no delta component (:447-448)
+                for (int i = 0; i < 3; i++) tr[i] = fastexp(sc.sigma_t[i] * (-t));
+                float mx = tr[0] > tr[1] ? tr[0] : tr[1];
+                mx = mx > tr[2] ? mx : tr[2];
+                if (mx < 1e-20f) tr[0] = tr[1] = tr[2] = 0;
+            }
+            if (!(tr[0] == 0 && tr[1] == 0 && tr[2] == 0)) {
+                F3 fs, ft;
+                frame_of(n, &fs, &ft);
+                const F3 mwi = f3(-cur.d.x, -cur.d.y, -cur.d.z);
+                const float cos_wi = dot(mwi, n);
+                float u[2] = {0.0f, 0.0f};
+                bool drawn = false;
+                int nd = 0;   // draws taken from this node's stream
+                const int ncomp = m == 3u ? 2 : 1;
+                CNode child[2];
+                bool live[2] = {false, false};
+                // the delta components (:467-511): at most 2
+                for (int c = 0; c < ncomp; c++) {
+                    float bw[3];
+                    float beta = 1.0f;   // bRec.eta
+                    F3 wol;
+                    if (m == 1u) {          // conductor.cpp:254-268
+                        if (cos_wi <= 0) continue;
+                        wol = f3(-dot(mwi, fs), -dot(mwi, ft), cos_wi);
+                        for (int i = 0; i < 3; i++) bw[i] = sc.occ_spec[i];
+                    } else if (m == 2u) {   // null.cpp:53-63
+                        wol = f3(-dot(mwi, fs), -dot(mwi, ft), -cos_wi);
+                        bw[0] = bw[1] = bw[2] = 1.0f;
+                    } else {                // dielectric.cpp:365-385, one component, ERadiance
+                        float cos_t;
+                        const float F = fresnel_dielectric_ext(cos_wi, &cos_t, sc.occ_eta);
+                        const float inv_eta = 1 / sc.occ_eta;
+                        if (c == 0) {
+                            wol = f3(-dot(mwi, fs), -dot(mwi, ft), cos_wi);
+                            bw[0] = bw[1] = bw[2] = F;
+                        } else {
+                            const float scale = -(cos_t < 0 ? inv_eta : sc.occ_eta);
+                            wol = f3(scale * dot(mwi, fs), scale * dot(mwi, ft), cos_t);
+                            beta = cos_t < 0 ? sc.occ_eta : inv_eta;
+                            const float factor = cos_t < 0 ? inv_eta : sc.occ_eta;
+                            bw[0] = bw[1] = bw[2] = factor * factor * (1 - F);
+                        }
+                        if (bw[0] == 0) continue;
+                    }
+                    // Russian roulette (:480-492)
+                    float thr2[3];
+                    for (int i = 0; i < 3; i++) thr2[i] = ((cur.thr[i] * tr[i]) * bw[i]) * (beta * beta);
+                    const float maxRR = cur.depth >= a.spec_rr_depth ? 0.98f : 1.0f;
+                    float mx = thr2[0] > thr2[1] ? thr2[0] : thr2[1];
+                    mx = mx > thr2[2] ? mx : thr2[2];
+                    const float rrProb = maxRR < mx ? maxRR : mx;
+                    if (rrProb <= 0) continue;
+                    if (rrProb < 1) {
+                        if (!drawn) { eye_draws(a.seed, a.pass, pixel, kw, u); drawn = true; }
+                        if (u[nd++] > rrProb) continue;
+                    }
+                    CNode& ch = child[c];
+                    for (int i = 0; i < 3; i++) {
+                        ch.thr[i] = thr2[i] / rrProb;
+                        ch.w[i] = ((cur.w[i] * tr[i]) * bw[i]) / rrProb;   // weight * transmittance * bsdfWeight / rrProb (:505)
+                    }
+                    ch.o = p;
+                    ch.d = add(add(mul(fs, wol.x), mul(ft, wol.y)), mul(n, wol.z));   // its.toWorld(bRec.wo)
+                    ch.depth = cur.depth + 1;
+                    live[c] = true;
+                }
+                if (live[0] && live[1]) {
+                    if (sp >= a.cap) return kChainOverflow;   // the entry point completes this pixel on the host
+                    chain_push(stack, lanes, lane, sp++, child[1]);
+                }
+                if (live[0]) { next = child[0]; alive = true; }
+                else if (live[1]) { next = child[1]; alive = true; }
+            }
+        }
+        if (!alive) {
+            if (sp == 0) break;
+            next = chain_pop(stack, lanes, lane, --sp);
+        }
+        cur = next;
+        mint = 1e-4f;   // RayDifferential(its.p, wo): mint = Epsilon
+    }
+    return k;
+}
+
+// count pass: counts[i] = records of pixel i's eye path (kChainOverflow: its
+// index is appended to ovf, *n_ovf counting them; at most n)
+// One launch covers pixels i0 .. i0 + lanes - 1 (those below n); the stack
+// workspace holds 'lanes' lanes.
+__global__ void __launch_bounds__(256) k_chain_count(TCam c, TScene sc, CArgs a, const uint32_t* __restrict__ pix,
+                                                     uint32_t i0, uint32_t lanes, uint32_t n,
+                                                     float* __restrict__ stack, uint32_t* __restrict__ counts,
+                                                     uint32_t* __restrict__ ovf, uint32_t* __restrict__ n_ovf)
+{
+    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lane >= lanes || lane >= n - i0) return;
+    const uint32_t i = i0 + lane;
+    const uint32_t id = pix ? pix[i] : i;
+    F3 O, D;
+    float mint;
+    sensor_ray(c, id, a.sample, a.spp, a.seed, a.pass, &O, &D, &mint);
+    const uint32_t k = chain_walk(sc, a, id, O, D, mint, stack, lanes, lane, nullptr, nullptr, nullptr, 0u, i);
+    counts[i] = k;
+    if (k == kChainOverflow) {
+        const uint32_t slot = atomicAdd(n_ovf, 1u);
+        if (slot < n) ovf[slot] = i;
+    }
+}
+
+// write pass: pixel i's records 1..counts[i]-1 at the positions pos[base[i]..]
+// the entry point derived from the counts; an overflowed pixel is the host's
+__global__ void __launch_bounds__(256) k_chain_write(TCam c, TScene sc, CArgs a, const uint32_t* __restrict__ pix,
+                                                     uint32_t i0, uint32_t lanes, uint32_t n,
+                                                     float* __restrict__ stack,
+                                                     const uint32_t* __restrict__ counts,
+                                                     const uint64_t* __restrict__ base,
+                                                     const uint32_t* __restrict__ pos, float* __restrict__ out,
+                                                     uint32_t* __restrict__ src)
+{
+    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lane >= lanes || lane >= n - i0) return;
+    const uint32_t i = i0 + lane;
+    const uint32_t cnt = counts[i];
+    if (cnt == kChainOverflow || cnt < 2u) return;
+    const uint32_t id = pix ? pix[i] : i;
+    F3 O, D;
+    float mint;
+    sensor_ray(c, id, a.sample, a.spp, a.seed, a.pass, &O, &D, &mint);
+    (void)chain_walk(sc, a, id, O, D, mint, stack, lanes, lane, out, src, pos + base[i], cnt, i);
+}
+
+// the host-completed pixels' records into their places: record j to out[pos[j]]
+__global__ void __launch_bounds__(256) k_chain_splice(const float* __restrict__ recs, const uint32_t* __restrict__ pos,
+                                                      const uint32_t* __restrict__ srcs, uint32_t m,
+                                                      float* __restrict__ out, uint32_t* __restrict__ src)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t d = pos[j];
+#pragma unroll
+    for (int q = 0; q < 20; q++) out[20 * (size_t)d + q] = recs[20 * (size_t)j + q];
+    src[d] = srcs[j];
 }
 
 // ----------------------------------------------------- volpath reference --
@@ -801,6 +1124,9 @@ TScene make_tscene(const alvrl::host::SmokeBox& box)
         sc.occ_albedo[i] = box.occ_albedo[i];
     }
     sc.occ_alb = nullptr;   // set by the caller that uploads box.occ_alb (upload_albedos)
+    sc.occ_mat = nullptr;   // set by the caller that uploads box.occ_mat (upload_materials)
+    for (int i = 0; i < 3; i++) sc.occ_spec[i] = box.occ_spec[i];
+    sc.occ_eta = box.occ_eta;
     sc.w = box.medium.sampling_weight;
     sc.strategy = box.medium.strategy;
     sc.density = box.medium.density;
@@ -864,6 +1190,16 @@ static bool upload_albedos(const alvrl::host::SmokeBox& box, DMem<float>& d, TSc
     return true;
 }
 
+// the occluders' BSDFs on the device (SmokeBox::occ_mat), for TScene::occ_mat
+static bool upload_materials(const alvrl::host::SmokeBox& box, DMem<uint32_t>& d, TScene& sc)
+{
+    if (!box.has_delta()) return true;   // all diffuse: no table
+    if (d.alloc(box.occ_mat.size()) != hipSuccess) return false;
+    if (hipMemcpy(d.p, box.occ_mat.data(), box.occ_mat.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
+    sc.occ_mat = d.p;
+    return true;
+}
+
 ALVRL_API int alvrl_volpath_render(const alvrl_scene_desc* s, const alvrl_volpath_params* p, uint32_t seed,
                                    uint32_t pass, uint32_t spp, const uint32_t* d_pixel_ids, uint32_t n,
                                    float* d_out_rgb, void* stream)
@@ -922,9 +1258,6 @@ ALVRL_API int alvrl_scene_records_spp_gpu(const alvrl_scene_desc* s, int medium_
         return terr(ALVRL_ERR_INVALID, "alvrl_scene_records_spp_gpu: spp out of range");
     if (const char* m = alvrl::host::scene_problem(*s)) return terr(ALVRL_ERR_INVALID, m);
     const alvrl::host::SmokeBox box = alvrl::host::to_box(*s);
-    if (box.has_delta())
-        return terr(ALVRL_ERR_INVALID, "alvrl_scene_records_gpu: mirror / null occluders: the eye paths are formed "
-                                       "on the host (alvrl_scene_records, the integrator's chain records)");
     const uint64_t npix = (uint64_t)box.width * (uint64_t)box.height;
     if (!d_pixel_ids && n > npix) return terr(ALVRL_ERR_INVALID, "alvrl_scene_records_gpu: n > W*H without pixel ids");
     if (n == 0) return ALVRL_OK;
@@ -935,6 +1268,8 @@ ALVRL_API int alvrl_scene_records_spp_gpu(const alvrl_scene_desc* s, int medium_
     sc.bv = bv->view;
     DMem<float> d_alb;
     if (!upload_albedos(box, d_alb, sc)) return terr(ALVRL_ERR_HIP, "alvrl_scene_records_gpu: albedo upload");
+    DMem<uint32_t> d_mat;
+    if (!upload_materials(box, d_mat, sc)) return terr(ALVRL_ERR_HIP, "alvrl_scene_records_gpu: material upload");
     const TCam c = make_tcam(box, medium_scatters && !sc.sigma_s_zero ? 1 : 0);
     hipStream_t st = (hipStream_t)stream;
     const uint32_t total = n * spp;
@@ -943,6 +1278,167 @@ ALVRL_API int alvrl_scene_records_spp_gpu(const alvrl_scene_desc* s, int medium_
     if (hipGetLastError() != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_records_gpu: launch");
     // stream-ordered callers may replace the cached BVH after return: wait for the kernel
     if (hipStreamSynchronize(st) != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_records_gpu: sync");
+    return ALVRL_OK;
+}
+
+// The device form of alvrl_scene_chain_spp for n pixels (include/alvrl_host.h).
+// Count pass, then the offsets on the host (per level, in pixel order), then
+// the write pass; pixels the count pass reports as overflowed are completed
+// by SmokeBox::make_chain and spliced in.
+ALVRL_API int alvrl_scene_chains_gpu(const alvrl_scene_desc* s, int medium_scatters, uint32_t seed, uint32_t pass,
+                                     int spec_rr_depth, float init_throughput, uint32_t sample, uint32_t spp,
+                                     const uint32_t* d_pixel_ids, uint32_t n, uint32_t stack_cap,
+                                     uint32_t* d_counts, uint32_t* level_off, uint32_t* n_levels,
+                                     alvrl_gather_rec* d_recs, uint32_t* d_src, uint64_t cap, uint64_t* total,
+                                     uint32_t* n_overflow, void* stream)
+{
+    using alvrl::host::kRecWords;
+    if (!s || !level_off || !n_levels || !total || (d_recs && !d_src))
+        return terr(ALVRL_ERR_INVALID, "alvrl_scene_chains_gpu: null argument");
+    if (spp == 0 || sample >= spp || spp > 0xFFFFu)
+        return terr(ALVRL_ERR_INVALID, "alvrl_scene_chains_gpu: sample out of range");
+    if (const char* m = alvrl::host::scene_problem(*s)) return terr(ALVRL_ERR_INVALID, m);
+    const alvrl::host::SmokeBox box = alvrl::host::to_box(*s);
+    const uint64_t npix = (uint64_t)box.width * (uint64_t)box.height;
+    if (!d_pixel_ids && n > npix) return terr(ALVRL_ERR_INVALID, "alvrl_scene_chains_gpu: n > W*H without pixel ids");
+    for (uint32_t d = 0; d <= ALVRL_CHAIN_MAX_LEVELS; d++) level_off[d] = 0;
+    *n_levels = 0;
+    *total = 0;
+    if (n_overflow) *n_overflow = 0;
+    if (n == 0) return ALVRL_OK;
+    TScene sc = make_tscene(box);
+    hipError_t be = hipSuccess;
+    const std::shared_ptr<DevBvh> bv = cached_bvh(box.occ, &be);
+    if (!bv) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: BVH upload");
+    sc.bv = bv->view;
+    DMem<float> d_alb;
+    if (!upload_albedos(box, d_alb, sc)) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: albedo upload");
+    DMem<uint32_t> d_mat;
+    if (!upload_materials(box, d_mat, sc)) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: material upload");
+    const bool scat = medium_scatters && !sc.sigma_s_zero;
+    const TCam c = make_tcam(box, scat ? 1 : 0);
+    CArgs a;
+    a.seed = seed; a.pass = pass; a.sample = sample; a.spp = spp;
+    a.flags = 1u | (scat ? 4u : 0u);
+    a.cap = stack_cap ? std::min(stack_cap, kChainStackMax) : kChainStackDefault;
+    a.spec_rr_depth = spec_rr_depth;
+    a.init_thr = init_throughput;
+    hipStream_t st = (hipStream_t)stream;
+    // the stack workspace serves one launch of at most 2^18 lanes at a time
+    const uint32_t lanes = std::min<uint32_t>(n, 1u << 18);
+    DMem<float> d_stack;
+    DMem<uint32_t> d_cnt, d_ovf, d_novf;
+    if (d_stack.alloc((size_t)lanes * a.cap * kChainNodeWords) != hipSuccess || d_cnt.alloc(n) != hipSuccess ||
+        d_ovf.alloc(n) != hipSuccess || d_novf.alloc(1) != hipSuccess)
+        return terr(ALVRL_ERR_NOMEM, "alvrl_scene_chains_gpu: device memory");
+    if (hipMemsetAsync(d_novf.p, 0, 4, st) != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: clear");
+    for (uint32_t i0 = 0; i0 < n; i0 += lanes) {
+        hipLaunchKernelGGL(k_chain_count, dim3((lanes + 255) / 256), dim3(256), 0, st, c, sc, a, d_pixel_ids, i0, lanes, n,
+                           d_stack.p, d_cnt.p, d_ovf.p, d_novf.p);
+        if (hipGetLastError() != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: launch");
+    }
+    std::vector<uint32_t> counts(n);
+    uint32_t novf = 0;
+    if (hipMemcpyAsync(counts.data(), d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&novf, d_novf.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: count pass");
+    novf = std::min(novf, n);
+    // the overflowed pixels' whole eye paths from the host (record 0 included)
+    std::vector<uint32_t> ovf(novf);
+    std::vector<std::vector<float>> ovf_recs(novf);
+    if (novf) {
+        if (hipMemcpy(ovf.data(), d_ovf.p, (size_t)novf * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: copy");
+        std::sort(ovf.begin(), ovf.end());
+        std::vector<uint32_t> ids;
+        if (d_pixel_ids) {
+            ids.resize(n);
+            if (hipMemcpy(ids.data(), d_pixel_ids, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: copy");
+        }
+        const uint32_t W = (uint32_t)box.width;
+        for (uint32_t j = 0; j < novf; j++) {
+            const uint32_t id = d_pixel_ids ? ids[ovf[j]] : ovf[j];
+            box.make_chain((int)(id % W), (int)(id / W), scat, seed, pass, spec_rr_depth, init_throughput, &ovf_recs[j],
+                           sample, spp);
+            counts[ovf[j]] = (uint32_t)(ovf_recs[j].size() / kRecWords);
+        }
+    }
+    if (n_overflow) *n_overflow = novf;
+    // level d holds record d + 1 of every pixel that has one, in pixel order
+    uint64_t hist[kChainMaxRecs + 1] = {0};
+    for (uint32_t i = 0; i < n; i++) hist[std::min(counts[i], kChainMaxRecs)]++;
+    uint64_t tot = 0, above = 0;
+    uint64_t lv[ALVRL_CHAIN_MAX_LEVELS + 1];
+    for (uint32_t d = ALVRL_CHAIN_MAX_LEVELS; d-- > 0;) {   // pixels with more than d + 1 records
+        above += hist[d + 2];
+        lv[d] = above;
+    }
+    uint32_t nl = 0;
+    for (uint32_t d = 0; d < ALVRL_CHAIN_MAX_LEVELS; d++) {
+        if (lv[d]) nl = d + 1;
+        tot += lv[d];
+    }
+    *total = tot;
+    if (tot > 0xFFFFFFFFull) return terr(ALVRL_ERR_INVALID, "alvrl_scene_chains_gpu: more than 2^32 records");
+    uint64_t run = 0;
+    for (uint32_t d = 0; d < ALVRL_CHAIN_MAX_LEVELS; d++) { level_off[d] = (uint32_t)run; run += lv[d]; }
+    level_off[ALVRL_CHAIN_MAX_LEVELS] = (uint32_t)run;
+    *n_levels = nl;
+    if (d_counts && hipMemcpy(d_counts, counts.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: copy");
+    if (!d_recs) return ALVRL_OK;   // size query
+    if (tot > cap) return terr(ALVRL_ERR_INVALID, "alvrl_scene_chains_gpu: capacity too small");
+    if (tot == 0) return ALVRL_OK;
+    // pos[base[i] + k - 1]: where record k of pixel i goes
+    std::vector<uint64_t> base(n);
+    std::vector<uint32_t> pos((size_t)tot), fill(level_off, level_off + ALVRL_CHAIN_MAX_LEVELS);
+    uint64_t b = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        base[i] = b;
+        for (uint32_t k = 1; k < counts[i]; k++) pos[(size_t)b++] = fill[k - 1]++;
+    }
+    DMem<uint64_t> d_base;
+    DMem<uint32_t> d_pos;
+    if (d_base.alloc(n) != hipSuccess || d_pos.alloc((size_t)tot) != hipSuccess)
+        return terr(ALVRL_ERR_NOMEM, "alvrl_scene_chains_gpu: device memory");
+    if (hipMemcpyAsync(d_base.p, base.data(), (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_pos.p, pos.data(), (size_t)tot * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+        return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: copy");
+    // d_cnt keeps kChainOverflow for the host's pixels: the write pass skips them
+    for (uint32_t i0 = 0; i0 < n; i0 += lanes) {
+        hipLaunchKernelGGL(k_chain_write, dim3((lanes + 255) / 256), dim3(256), 0, st, c, sc, a, d_pixel_ids, i0, lanes, n,
+                           d_stack.p, d_cnt.p, d_base.p, d_pos.p, reinterpret_cast<float*>(d_recs), d_src);
+        if (hipGetLastError() != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: launch");
+    }
+    DMem<float> d_hrec;
+    DMem<uint32_t> d_hpos, d_hsrc;
+    std::vector<float> hrec;
+    std::vector<uint32_t> hpos, hsrc;
+    for (uint32_t j = 0; j < novf; j++) {
+        const uint32_t i = ovf[j];
+        for (uint32_t k = 1; k < counts[i]; k++) {
+            hrec.insert(hrec.end(), ovf_recs[j].begin() + (size_t)k * kRecWords,
+                        ovf_recs[j].begin() + (size_t)(k + 1) * kRecWords);
+            hpos.push_back(pos[(size_t)base[i] + k - 1]);
+            hsrc.push_back(i);
+        }
+    }
+    if (!hpos.empty()) {
+        const uint32_t m = (uint32_t)hpos.size();
+        if (d_hrec.alloc(hrec.size()) != hipSuccess || d_hpos.alloc(m) != hipSuccess || d_hsrc.alloc(m) != hipSuccess)
+            return terr(ALVRL_ERR_NOMEM, "alvrl_scene_chains_gpu: device memory");
+        if (hipMemcpyAsync(d_hrec.p, hrec.data(), hrec.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d_hpos.p, hpos.data(), (size_t)m * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d_hsrc.p, hsrc.data(), (size_t)m * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+            return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: copy");
+        hipLaunchKernelGGL(k_chain_splice, dim3((m + 255) / 256), dim3(256), 0, st, d_hrec.p, d_hpos.p, d_hsrc.p, m,
+                           reinterpret_cast<float*>(d_recs), d_src);
+        if (hipGetLastError() != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: launch");
+    }
+    // the workspace and the cached BVH may go after return: wait for the kernels
+    if (hipStreamSynchronize(st) != hipSuccess) return terr(ALVRL_ERR_HIP, "alvrl_scene_chains_gpu: sync");
     return ALVRL_OK;
 }
 
@@ -956,8 +1452,6 @@ ALVRL_API int alvrl_trace_vrls_gpu(const alvrl_scene_desc* s, uint32_t seed, uin
     // the scene as the host tracer resolves it (to_box + MediumParams::resolve)
     if (const char* m = alvrl::host::scene_problem(*s)) return terr(ALVRL_ERR_INVALID, m);
     const alvrl::host::SmokeBox box = alvrl::host::to_box(*s);
-    if (box.has_delta())
-        return terr(ALVRL_ERR_INVALID, "alvrl_trace_vrls_gpu: mirror / null occluders are traced on the host (alvrl_trace_vrls)");
     TScene sc = make_tscene(box);
     hipError_t be = hipSuccess;
     const std::shared_ptr<DevBvh> bvh = cached_bvh(box.occ, &be);
@@ -965,6 +1459,8 @@ ALVRL_API int alvrl_trace_vrls_gpu(const alvrl_scene_desc* s, uint32_t seed, uin
     sc.bv = bvh->view;
     DMem<float> d_alb;
     if (!upload_albedos(box, d_alb, sc)) return terr(ALVRL_ERR_HIP, "alvrl_trace_vrls_gpu: albedo upload");
+    DMem<uint32_t> d_mat;
+    if (!upload_materials(box, d_mat, sc)) return terr(ALVRL_ERR_HIP, "alvrl_trace_vrls_gpu: material upload");
     const TArgs a{seed, pass, short_vrls, max_depth, rr_depth};
     *n = 0;
     if (target == 0) { *particles = 0; return ALVRL_OK; }
