@@ -5,11 +5,11 @@
 // on a segment for the shadow tests of Scene::evalTransmittance
 // (scene.cpp:619-679).
 //
-// The triangle test has the host's operation order (csrc/host/scene.cpp
-// tri_intersect); in translation units built with -ffp-contract=off and IEEE
-// division (tracer.hip) it returns the host's t bit for bit, and the closest
-// hit takes the smallest t, ties to the lowest triangle index, which is what
-// the host's loop in index order finds.  Traversal: a per-lane stack, the
+// The triangle test is the host's (vec3.h tri_intersect); in translation
+// units built with -ffp-contract=off and IEEE division (tracer.hip) it returns
+// the host's t bit for bit, and the closest hit takes the smallest t, ties to
+// the lowest triangle index, which is what the host's loop in index order
+// finds.  Traversal: a per-lane stack, the
 // nearer child first; a node is skipped only if its (padded) slab interval
 // misses [mint, best] -- a node at exactly the best t is still visited so
 // that ties resolve by index.
@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "host/bvh.hpp"
+#include "vec3.h"
 
 namespace alvrl {
 namespace bvh {
@@ -31,34 +32,9 @@ struct View {
     uint32_t ntri;
 };
 
-struct V { float x, y, z; };
+using V = transport::V3;
+using transport::tri_intersect;
 __device__ __forceinline__ V mk(float x, float y, float z) { return V{x, y, z}; }
-__device__ __forceinline__ V sub(V a, V b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ float dot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V cross(V a, V b)
-{
-    return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
-
-__device__ __forceinline__ bool tri_intersect(const float* q, V o, V d, float* u, float* v, float* t)
-{
-    const V p0 = mk(q[0], q[1], q[2]), p1 = mk(q[3], q[4], q[5]), p2 = mk(q[6], q[7], q[8]);
-    const V edge1 = sub(p1, p0), edge2 = sub(p2, p0);
-    const V pvec = cross(d, edge2);
-    const float det = dot(edge1, pvec);
-    if (det == 0) return false;
-    const float inv_det = 1.0f / det;
-    const V tvec = sub(o, p0);
-    *u = dot(tvec, pvec) * inv_det;
-    if (*u < 0.0f || *u > 1.0f) return false;
-    const V qvec = cross(tvec, edge1);
-    *v = dot(d, qvec) * inv_det;
-    if (*v >= 0.0f && *u + *v <= 1.0f) {
-        *t = dot(edge2, qvec) * inv_det;
-        return true;
-    }
-    return false;
-}
 
 // slab interval of a padded node box intersected with [tmin, tmax]
 __device__ __forceinline__ bool slab(const BvhNode& nd, V o, V inv, float tmin, float tmax, float* tnear)

@@ -14,41 +14,10 @@
 namespace alvrl {
 namespace host {
 
+using transport::kDomReps;
+using transport::Stream;
+
 namespace {
-constexpr uint32_t kDomReps = 4u;
-
-void philox(const uint32_t ctr_in[4], const uint32_t key_in[2], uint32_t out[4])
-{
-    uint32_t c0 = ctr_in[0], c1 = ctr_in[1], c2 = ctr_in[2], c3 = ctr_in[3];
-    uint32_t k0 = key_in[0], k1 = key_in[1];
-    for (int r = 0; r < 10; r++) {
-        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-struct Stream {
-    uint32_t seed, pass, dom, a, b, c, k = 0, blk = 0xFFFFFFFFu;
-    uint32_t buf[4];
-    float next()
-    {
-        const uint32_t bl = k >> 2;
-        if (bl != blk) {
-            const uint32_t ctr[4] = {a, b, bl, (dom << 24) | (c & 0xFFFFFFu)};
-            const uint32_t key[2] = {seed, pass};
-            philox(ctr, key, buf);
-            blk = bl;
-        }
-        union { uint32_t u; float f; } x;
-        x.u = (buf[k & 3] >> 9) | 0x3f800000u;
-        ++k;
-        return x.f - 1.0f;
-    }
-};
-
 float slice_distance(V3 p1, V3 d1, V3 p2, V3 d2)   // Preprocessor.cpp:1230-1234
 {
     const float dx = p1.x - p2.x, dy = p1.y - p2.y, dz = p1.z - p2.z;
@@ -220,7 +189,7 @@ void Preprocessor::sample_slice_mapping(float targetUnder)
         const uint32_t* gp = m_idx.data() + m_lo[s];
         size_t target = (size_t)(0.5 + (double)((float)np / targetUnder));
         if (target < 2) target = std::min((size_t)2, np);
-        Stream smp{m_p.seed, m_p.pass, kDomReps, s, 0u, 0u};
+        Stream smp(m_p.seed, m_p.pass, kDomReps, s, 0u);
         if (np <= target) {
             for (size_t i = 0; i < np; i++) m_rep_pix.push_back(gp[i]);
         } else if (np <= 2 * target) {
